@@ -45,6 +45,7 @@ FP32_MATRIX_PEAK = 157.3    # native fp32 MFMA TFLOP/s (the pipe an fp32 GEMM wo
 GEMM_NAMES = ("gemm_nt", "gemm_tn", "gemm_nt_pair", "gemm_tn_pair", "gemm_nt_bf16", "gemm_tn_bf16", "gemm_nt_skinny")
 HELPER_NAMES = ("absmax", "split_rows")
 GAT_PREFIXES = ("gat_fwd", "gat_bwd", "gat_agg", "lspe_")
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
 # roofline.traffic is NOT measured by this run: PMC counters need rocprofv3 passes of their own
 TRAFFIC_SOURCE = "profiles/traffic_latest.json (builder's rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this step, per launch; not measured in this run)"
 
@@ -261,10 +262,37 @@ def pct(xs, q):
     return xs[min(len(xs) - 1, max(0, int(round(q * (len(xs) - 1)))))]
 
 
+def dump_outputs(out_dir, model, step, loss, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: what the timed path computed in its LAST timed step, as a caller of TrainStep receives it - the loss
+    and every trainable parameter's updated weights, gradient and momentum buffer (views of the flat bucket) - one float32
+    ``<out_dir>/<name>.npy`` each.  Inputs are seeded, so two builds run with the same arguments can be compared file by file.
+    Beyond ``cap_bytes`` in all, every array is cut to the same fraction by a fixed seeded sample of its flat elements."""
+    import numpy as np
+    names = {id(p): n for n, p in model.named_parameters()}
+    b = step.bucket
+    arrays = {"loss": loss.detach().reshape(1)}
+    for p, off in zip(b.params, b.offsets):
+        n, name = p.numel(), names[id(p)]
+        for kind, flat in (("param", b.flat_param), ("grad", b.flat_grad), ("momentum", b.flat_mom)):
+            arrays[f"{kind}.{name}"] = flat[off:off + n].view(p.shape)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    frac = min(1.0, cap_bytes / total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, max(1, int(flat.size * frac)), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays)
+
+
 def run_leg(config, dtype, trees, steps, warmup, *, rank, world, dev, eager=False, no_eager_leg=False, no_dropout=False,
-            no_kernel_timers=False, copy_bw=None, heads=0, loss_rows=False, exchange=None):
+            no_kernel_timers=False, copy_bw=None, heads=0, loss_rows=False, exchange=None, dump_dir=None):
     """One measured workload: build the model and the batch, warm up, capture, time ``steps`` steps between barrier +
-    synchronize, then the instrumented eager leg.  -> (the JSON object on rank 0 else None, (cfg, model, samples))."""
+    synchronize, [dump the last timed step's outputs to ``dump_dir``], then the instrumented eager leg.
+    -> (the JSON object on rank 0 else None, (cfg, model, samples))."""
     from spgnn_amd import _capi, models, ops, synthetic
     from spgnn_amd.configs import class_weight_list, get_config
     from spgnn_amd.train import TrainStep
@@ -375,6 +403,8 @@ def run_leg(config, dtype, trees, steps, warmup, *, rank, world, dev, eager=Fals
         gc.enable()
         if comm_ev is not None:
             step._reduce = plain_reduce
+    if dump_dir is not None and rank == 0:          # before the eager leg below takes more steps on the same model
+        dump_outputs(dump_dir, model, step, loss)
     comm = None
     if exchange:
         ar_ms = sorted(a.elapsed_time(b) for a, b in comm_ev) if comm_ev is not None else []
@@ -453,7 +483,8 @@ def run_leg(config, dtype, trees, steps, warmup, *, rank, world, dev, eager=Fals
                        "trees_per_gpu": trees, "global_trees": trees * world, "nodes": int(N_all),
                        "edges": int(E_all), "conv_layers": L, "trainable_params": n_params,
                        "parallelism": f"dp{world}", "launch": launch, "gemm": gemm_desc,
-                       "weight_gradients_on_side_stream": bool(ops.OVERLAP_TN and N >= ops.OVERLAP_TN_MIN_ROWS)},
+                       "weight_gradients_on_side_stream": bool(ops.OVERLAP_TN and N >= ops.OVERLAP_TN_MIN_ROWS
+                                                                              and (launch == "eager" or ops.OVERLAP_TN_IN_GRAPHS))},
             "graph_edges_per_s": E_all * steps / elapsed, "loss": loss_val,
             "step_ms": {"median": pct(step_ms, 0.5), "p10": pct(step_ms, 0.1), "p90": pct(step_ms, 0.9),
                         "n": len(step_ms), "how": "HIP events on the compute stream around every timed step (rank 0)"},
@@ -1109,6 +1140,9 @@ def main():
     ap.add_argument("--cpu-small-sample", action="store_true", help="cpu_baseline: also time the 64-tree sample of rounds 1-4 (value64)")
     ap.add_argument("--count-launches", action="store_true", help="single-tree leg: count all device launches of a forward with torch.profiler")
     ap.add_argument("--graph", action="store_true", help="(default) kept for older command lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss and every trainable parameter's weights, gradient and momentum of the "
+                         "last timed step as DIR/<name>.npy (float32, <= 64 MB in all; rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1154,7 +1188,7 @@ def main():
     out, (cfg, model, samples) = run_leg(args.config, args.dtype, args.trees, args.steps, args.warmup, rank=rank, world=world, dev=dev,
                                          eager=args.eager, no_eager_leg=args.no_eager_leg, no_dropout=args.no_dropout,
                                          no_kernel_timers=args.no_kernel_timers, heads=args.heads, loss_rows=("backward" if args.loss_rows_backward else args.loss_rows_only),
-                                         exchange=exchange)
+                                         exchange=exchange, dump_dir=args.dump_outputs)
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, model, samples, min(args.cpu_trees, args.trees) if args.cpu_trees else args.trees,

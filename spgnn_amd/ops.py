@@ -321,6 +321,10 @@ TN_SIDE: Optional["SideLaunch"] = None      # traversals that follow; installed 
 OVERLAP_TN_MIN_ROWS = 32768    # ... for batches of at least this many nodes.  One process, alternating (tools/step_toggle_ab.py, MI355X,
                                # round 5): st_pgat_spgnn_3 4.990 / 4.980 vs 5.058 / 5.037 ms at 512 trees (-1.2 %), st_gat_3 2.880 vs 2.903;
                                # at 64 trees 1.027 vs 1.003 (the fork and join cost more than the short products hide): off there
+OVERLAP_TN_IN_GRAPHS = False   # ... also inside a captured step (the side stream as a parallel branch of its HIP graph).  Off: on the
+                               # ROCm 7.2 HIP runtime, replaying a captured step with that branch segfaults on the host inside
+                               # hipGraphLaunch, while the same step without it replays cleanly and eager steps keep the side stream.
+                               # The results are the same either way (tests/test_hip_models.py::test_side_stream_weight_gradients_...).
 
 
 def side_for(rows: int, device) -> Optional["SideLaunch"]:
@@ -334,7 +338,7 @@ class SideLaunch:
     reads a weight gradient, while the input-gradient product and the next level's traversals are on the critical path: an
     MFMA-bound product and the HBM-bound traversals use different parts of the chip, and issued on two streams they overlap
     (tools/overlap_probe.py, MI355X: a 558 us weight-gradient product next to 864 us of GAT traversals: 1 283 us against 1 389
-    one after the other).  Under capture the side stream becomes a parallel branch of the step's HIP graph.  Tensors the side
+    one after the other).  Under capture (only with OVERLAP_TN_IN_GRAPHS) the side stream becomes a parallel branch of the step's HIP graph.  Tensors the side
     launches read are kept alive here until ``join()``: the caching allocator may otherwise hand their memory to a later
     allocation of the main stream while the product still reads it."""
 

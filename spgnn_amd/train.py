@@ -335,9 +335,10 @@ class TrainStep:
         # step): the deferred outputs start as NaN, so whatever autograd copied, added or handed to a hook before the flush shows
         # up as a NaN in the gathered bucket (one host read, once).  Never under stream capture.
         verify = bool(sums is not None and self._verify_deferred and not torch.cuda.is_current_stream_capturing())
-        # the weight-gradient products go to a side stream and overlap the traversals that follow them (ops.SideLaunch)
+        # the weight-gradient products go to a side stream and overlap the traversals that follow them (ops.SideLaunch);
+        # in eagerly issued steps only unless ops.OVERLAP_TN_IN_GRAPHS (see there)
         side = None
-        if on_gpu and ops.OVERLAP_TN:
+        if on_gpu and ops.OVERLAP_TN and (ops.OVERLAP_TN_IN_GRAPHS or not torch.cuda.is_current_stream_capturing()):
             if getattr(self, "_tn_side", None) is None:
                 self._tn_side = ops.SideLaunch(b.flat_param.device)
             side = self._tn_side

@@ -850,7 +850,7 @@ def test_side_stream_weight_gradients_are_bit_identical(name, trees, min_rows, m
     """ops.SideLaunch (round 5): a training step issues its weight-gradient products on a side stream, behind the input-gradient
     products, so that they run next to the following level's traversals.  Only the ORDER of launches and the stream change:
     the flat gradient bucket and the parameters after two steps are bit for bit those of the single-stream step - eagerly issued
-    and as HIP-graph replays (the side stream is a parallel branch of the captured step) - with the deferred outputs poisoned
+    and as HIP-graph replays (which leave the side stream out unless ops.OVERLAP_TN_IN_GRAPHS) - with the deferred outputs poisoned
     with NaN so that a sum reading a partial before the join could not pass."""
     from spgnn_amd import ops as _ops
     cfg, model = _build(name, seed=17)

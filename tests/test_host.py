@@ -106,11 +106,16 @@ def test_ops_refuse_cpu_tensors():
         snn.GraphConv(4, 2)(g, torch.randn(2, 4))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/exp_settings"), reason="reference checkout not present")
 def test_embedded_configs_equal_reference_settings():
+    """tests/golden/reference_settings.json holds, per config, the settings values of the reference's
+    exp_settings/<name>.py that the embedded configs mirror (each value as a Python literal, so tuples and int keys survive)."""
+    import ast
+    from types import SimpleNamespace
     from spgnn_amd import configs as c
+    stored = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_settings.json")))
+    assert sorted(stored) == sorted(c.CONFIGS)
     for name, mine in c.CONFIGS.items():
-        s = c.load_settings(f"/root/reference/exp_settings/{name}.py")
+        s = SimpleNamespace(**{k: ast.literal_eval(v) for k, v in stored[name].items()})
         ref_model = dict(s.MODEL)
         if name == "st_pgat_spgnnnl_3":      # the reference names a class that does not exist (SURVEY.md §0)
             assert ref_model.pop("method") == "models.GATPositionLSPENet"
@@ -580,6 +585,33 @@ def test_bench_prints_exactly_one_stdout_line_and_writes_the_detail_file(tmp_pat
     os.remove(got)
     got = bench.write_detail({"a": 1}, str(tmp_path / "d.json"))
     assert got == str(tmp_path / "d.json") and json.load(open(got)) == {"a": 1}
+
+
+def test_bench_dump_outputs_writes_the_steps_state(tmp_path):
+    """--dump-outputs: loss + every trainable parameter's weights / gradient / momentum, float32, one .npy each; over the cap
+    every array is cut by the same fixed seeded sample, so two runs write identical files."""
+    from types import SimpleNamespace
+    from spgnn_amd.train import FlatBucket
+    bench = _load_bench()
+    model = torch.nn.Sequential(torch.nn.Linear(5, 3), torch.nn.Linear(3, 2, bias=False))
+    b = FlatBucket(list(model.parameters()))
+    b.flat_grad.copy_(torch.arange(b.flat_grad.numel(), dtype=torch.float32))
+    b.flat_mom.fill_(-1.0)
+    step = SimpleNamespace(bucket=b)
+    n = bench.dump_outputs(str(tmp_path / "full"), model, step, torch.tensor(0.5))
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "full"))
+    assert n == len(names) == 1 + 3 * 3 and "loss" in names
+    assert np.load(tmp_path / "full" / "loss.npy").tolist() == [0.5]
+    w = np.load(tmp_path / "full" / "param.0.weight.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, model[0].weight.detach().numpy())
+    assert np.array_equal(np.load(tmp_path / "full" / "grad.1.weight.npy"), model[1].weight.grad.numpy())
+    assert (np.load(tmp_path / "full" / "momentum.0.bias.npy") == -1.0).all()
+    for d in ("cut_a", "cut_b"):
+        bench.dump_outputs(str(tmp_path / d), model, step, torch.tensor(0.5), cap_bytes=64)
+    total = sum(np.load(tmp_path / "cut_a" / f).nbytes for f in os.listdir(tmp_path / "cut_a"))
+    assert total <= 64
+    for f in os.listdir(tmp_path / "cut_a"):
+        assert np.array_equal(np.load(tmp_path / "cut_a" / f), np.load(tmp_path / "cut_b" / f))
 
 
 def test_bench_launcher_never_touches_torch_cuda_and_runs_forced_with_one_rank():
