@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SPGNN_ABI_VERSION 63
+#define SPGNN_ABI_VERSION 64
 
 #define SPGNN_OK            0
 #define SPGNN_ERR_NULLPTR  -1
@@ -1294,6 +1294,36 @@ typedef struct spgnn_sum_job {
   float* extra; int32_t extra_col; int32_t reserved;
 } spgnn_sum_job;
 int spgnn_sum_partials_multi(const spgnn_sum_job* jobs, int32_t n_jobs, spgnn_stream_t stream);
+
+/*
+ * ABI 64.  Auxiliary losses on the position stream p of the SPGNN training step (reference job_runner.py:1827-1865
+ * dist_pos_loss, on when USE_DIST_LOSS; csrc/spgnn_posloss.hip).
+ *
+ * spgnn_pos_loss_tables - once per loader batch, one workgroup per tree: dist[dist_off[t] + i * n_t + j] = hop distance of
+ * local nodes i, j of tree t (uint16; BFS parent / depth arrays in LDS, then the lowest common ancestor of every pair),
+ * diameters[t] = its maximum, label_node[t * num_labels + L - 1] = GLOBAL id of the node of tree t with label L and the
+ * highest index (-1: label absent).  out_indptr / out_indices: CSR of the batched graph (both directions of every tree
+ * edge; self loops ignored); tree_ptr[num_trees + 1] node offsets; labels (num_nodes) int64.  Trees of at most 2048 nodes.
+ *
+ * spgnn_pos_losses - per step, two launches, no atomics, fixed summation order:
+ *   d = mean_t mean_{i,j} smooth_l1(exp(-|p_i - p_j|_1), exp(-dist_ij / diam_t)),
+ *   c = mean_t sum_L |p[label_node[t, L]] - mean[L]|^2 (0 while state[0] == 0),
+ *   g_p rows of every node of the trees = weight_sum * d(d + c_weight * c)/dp (pad rows are not written),
+ *   mean <- batch mean of the label rows (absent labels: uniform [0,1) counter-hash noise of (seed, state[0], t, L, k)) on the
+ *   first step, else 0.15 mean + 0.85 batch mean;  losses[0..1] = d, c;  loss_num[0] (nullable) += weight_sum * (d + c_weight * c);
+ *   state[0] += 1 (state: int64[2], state[1] is scratch).  weight_sum (nullable: 1) is read on the device.
+ * blocks: (num_blocks, 2) int32 (tree, first local row) of 64-row blocks covering every tree; tree -1 marks an unused block.
+ * num_trees_dev: the tree count (int32, on the device, <= max_trees); max_tree_nodes bounds n_t (LDS: n_t * (D <= 40 ? 41 : 65)
+ * floats <= 160 KiB).  D = p's width, 1..64; mean: (num_labels, D); partials: num_blocks * 2 floats.
+ */
+int spgnn_pos_loss_tables(const int32_t* out_indptr, const int32_t* out_indices, const int64_t* tree_ptr, const int64_t* dist_off,
+                          const int64_t* labels, int32_t num_labels, int64_t num_trees, int64_t max_tree_nodes, uint16_t* dist,
+                          int32_t* diameters, int32_t* label_node, spgnn_stream_t stream);
+int spgnn_pos_losses(const float* p, int64_t p_stride, int32_t D, const int64_t* labels, const int64_t* tree_ptr, const int64_t* dist_off,
+                     const uint16_t* dist, const int32_t* diameters, const int32_t* label_node, int32_t num_labels, const int32_t* blocks,
+                     int32_t num_blocks, const int32_t* num_trees_dev, int64_t max_trees, int64_t max_tree_nodes, float* mean,
+                     int64_t* state, uint64_t seed, const float* weight_sum, float c_weight, float* g_p, int64_t g_p_stride,
+                     float* partials, float* loss_num, float* losses, spgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libspgnn_hip.so")
-ABI_VERSION = 63
+ABI_VERSION = 64
 
 _i32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 _f32p = C.c_void_p
@@ -246,6 +246,9 @@ SIGNATURES = {
     "spgnn_weight_cat_bf16_blocks": [_i32, _i32, _i64, _i64, _vp],
     "spgnn_weight_cat_bf16_multi": [_vp, _i32, _i32, _vp],
     "spgnn_cast_rows_bf16": [_f32p, _i64, _i64, _i32, _vp, _i64, _vp],
+    "spgnn_pos_loss_tables": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp],
+    "spgnn_pos_losses": [_f32p, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _i64, _f32p, _vp, _u64, _f32p, _f32,
+                         _f32p, _i64, _f32p, _f32p, _f32p, _vp],
 }
 
 _lib: Optional[C.CDLL] = None

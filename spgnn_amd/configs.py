@@ -56,15 +56,21 @@ CONFIGS: Dict[str, dict] = {
                              "feat_drop": 0.1, "node_sample_rate": 0.3, "num_hiddens": [256, 128, 64]},
                       SAMPLING_RATE=0.05, POS_ENC_DIM=None, KIND="sage", CONV_LAYERS=4, **_OPT),
     # exp_settings/st_pgat_spgnn_3.py:27,86-115 ; st_pgat_spgnnnl_3.py (mode PENL)
-    "st_pgat_spgnn_3": dict(MODEL=dict(_SPGNN), SAMPLING_RATE=0.15, POS_ENC_DIM=39, KIND="spgnn_pel", CONV_LAYERS=7, **_OPT),
+    # USE_DIST_LOSS / LAMBDA: st_pgat_spgnn_3.py:44,83 and st_pgat_spgnnnl_3.py:42,81 (train.TrainStep(pos_losses=USE_DIST_LOSS))
+    "st_pgat_spgnn_3": dict(MODEL=dict(_SPGNN), SAMPLING_RATE=0.15, POS_ENC_DIM=39, KIND="spgnn_pel", CONV_LAYERS=7,
+                            USE_DIST_LOSS=False, LAMBDA=1e-1, **_OPT),
     "st_pgat_spgnnnl_3": dict(MODEL={**_SPGNN, "mode": "PENL"}, SAMPLING_RATE=0.15, POS_ENC_DIM=39, KIND="spgnn_penl",
-                              CONV_LAYERS=4, **_OPT),
+                              CONV_LAYERS=4, USE_DIST_LOSS=False, LAMBDA=1e-1, **_OPT),
 }
+
+
+# settings every config exposes, with the value a reference settings file that does not set them implies
+_DEFAULTS = dict(USE_DIST_LOSS=False)
 
 
 def get_config(name: str) -> SimpleNamespace:
     import copy
-    return SimpleNamespace(**copy.deepcopy(CONFIGS[name]), NAME=name)
+    return SimpleNamespace(**{**_DEFAULTS, **copy.deepcopy(CONFIGS[name])}, NAME=name)
 
 
 def load_settings(path: str) -> SimpleNamespace:
@@ -72,7 +78,7 @@ def load_settings(path: str) -> SimpleNamespace:
     spec = importlib.util.spec_from_file_location("settings", path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    ns = SimpleNamespace(**{k: getattr(mod, k) for k in dir(mod) if k.isupper()})
+    ns = SimpleNamespace(**{**_DEFAULTS, **{k: getattr(mod, k) for k in dir(mod) if k.isupper()}})
     ns.settings_module_path = path
     return ns
 

@@ -145,7 +145,8 @@ class TrainStep:
 
     def __init__(self, model: torch.nn.Module, class_weights: Sequence[float], sampling_rate: float, lr: float,
                  momentum: float = 0.9, weight_decay: float = 0.0, process_group=None, seed: int = 0,
-                 range_policy: str = "monitor", loss_rows_only: bool = False, always_exchange: bool = False):
+                 range_policy: str = "monitor", loss_rows_only: bool = False, always_exchange: bool = False,
+                 pos_losses: bool = False):
         """``loss_rows_only``: run what follows the last aggregation - output-layer projection, head mean, classifier and their
         backward products - only on the rows the step's mask keeps (``F.cross_entropy(pre[mask], ...)``, reference
         job_runner.py:1896-1900: no other row reaches the loss or a gradient).  Same loss and gradients up to fp32 summation
@@ -157,6 +158,10 @@ class TrainStep:
         ``always_exchange``: issue the step's all-reduce (and split the captured step in two graphs around it) even when the
         process group has ONE rank - the multi-rank step with nothing to add, which lets a one-GPU box exercise the RCCL path
         (bench.py, SPGNN_BENCH_FORCE_LAUNCH).
+        ``pos_losses``: the reference's USE_DIST_LOSS (job_runner.py:1901-1903): the loss becomes ``CE + d + 0.1 c`` with the
+        distance-preserving and compactness terms on the position stream's output (spgnn_amd/posloss.py; one HIP pass after the
+        loss sums, its gradient seeds the backward pass next to the logits').  One process, the PEL SPGNN net only; ``d`` and
+        ``c`` of the last step: :attr:`last_pos_losses`; the running mean of the label rows is part of :meth:`state_dict`.
         ``range_policy``: what :meth:`run_batch` does with the GEMM range monitor: "monitor" only
         counts (``range_violations()``); "auto" switches the split GEMMs to their wide-range form (``ops.GEMM_WIDE``) for all
         later batches once an operand left the narrow envelope, dropping the captures recorded in the narrow form."""
@@ -187,6 +192,48 @@ class TrainStep:
         self._rows_cnt = None                       # (2,) int32 on the device: [rows kept by the last step, capacity-overflow flag]
         self._skipped = None                        # (1,) int32 on the device: steps the guarded SGD kernel did not apply (non-finite loss)
         self._rows_headroom, self._rows_gen = 1.0, 0    # capacity factor / generation of the per-graph capacity caches
+        self.pos_losses = bool(pos_losses)
+        self._pos = None                            # posloss.PosLossState (created at the first step: p's width is known then)
+        self._pos_seed = int(seed)
+        if self.pos_losses:
+            self._check_pos_losses(model, loss_rows_only)
+
+    def _check_pos_losses(self, model, loss_rows_only) -> None:
+        from .models import GATPositionSPGNNNet
+        if not isinstance(model, GATPositionSPGNNNet) or getattr(model, "mode", None) != "PEL":
+            raise NotImplementedError("pos_losses=True (USE_DIST_LOSS) is implemented for the PEL SPGNN net "
+                                      "(GATPositionSPGNNNet, mode 'PEL') only")
+        if self.world > 1:
+            raise NotImplementedError("pos_losses=True with more than one rank: the class-weight sum that scales the seed gradient "
+                                      "is only known after the all-reduce (single process only for now)")
+        if loss_rows_only:
+            raise NotImplementedError("pos_losses=True together with loss_rows_only is not supported")
+
+    @property
+    def last_pos_losses(self):
+        """(d, c) of the last step as device scalars (None before the first step or with ``pos_losses=False``)."""
+        if self._pos is None:
+            return None
+        return self._pos.losses[0], self._pos.losses[1]
+
+    def _pos_tables(self, g):
+        from . import posloss
+        t = posloss.PosLossTables.of(g)
+        hooked = g.__dict__.setdefault("_pos_loss_hooked", set())
+        if getattr(g, "_stable_storage", False) and id(self) not in hooked:
+            # one hook per (step object, arena graph), whoever created the tables; it runs after the tables' own reload hook:
+            # storage that had to grow has new addresses - drop this step's capture made on the old ones
+            hooked.add(id(self))
+            seen = [t.gen]
+
+            def check():
+                if t.gen != seen[0]:
+                    seen[0] = t.gen
+                    self._captures.pop(id(g), None)
+                    if self._captured_graph is g:
+                        self._graph = self._graph_back = self._captured_graph = None
+            g._refresh_hooks.append(check)
+        return t
 
     def _loss_rows_cap(self, g, p: torch.Tensor) -> int:
         """Capacity of the step's row list on ``g``: the kept count is (labelled nodes) + Binomial(others, rate) - mean plus
@@ -368,17 +415,29 @@ class TrainStep:
                 head = ops.LossHead(y, p, draws, draw_seed, self.class_weight, b.sums_slot,
                                     flag=self._rows_cnt if rows is not None else None)
             ops.LOSS_HEAD = head
-            logits = self.model(g)[0]
+            outs = self.model(g)
+            logits = outs[0]
             ops.LOSS_ROWS = None
             ops.LOSS_HEAD = None
             if rows is not None and not rows.used:
                 rows = None                  # this model's head does not take the list: its logits have one row per node
                 self._rows_not_taken = True  # (a property of the model: later steps do not make the list)
             direct = logits.is_cuda
+            roots, seeds = [], []
+            if self.pos_losses:
+                if not direct:
+                    raise NotImplementedError("pos_losses=True needs the model on a ROCm device")
+                pos_p = outs[2]
+                if self._pos is None:
+                    from . import posloss
+                    self._pos = posloss.PosLossState(pos_p.shape[1], pos_p.device, seed=self._pos_seed)
+                    if getattr(self, "_pos_pending", None) is not None:
+                        self._pos.load_state_dict(self._pos_pending)
+                        self._pos_pending = None
             if head is not None and head.used:
                 # sums already in the bucket's tail; the stored gradient of the numerator starts the backward pass
                 num, den = b.loss_slot, b.wsum_slot
-                torch.autograd.backward(logits, head.g_logits)
+                roots, seeds = [logits], [head.g_logits]
             elif direct:                     # one kernel: mask, log-softmax, weighted NLL sums and the gradient; the two sums
                 nd = ops.masked_ce_sums(logits, y, draws, p, self.class_weight, out=b.sums_slot, draw_seed=draw_seed,
                                         unit_grad=True, rows=rows if (rows is not None and rows.forward) else None,
@@ -386,10 +445,17 @@ class TrainStep:
                 num, den = nd[0], nd[1]
                 if self._one is None or self._one.device != num.device:
                     self._one = torch.ones((), dtype=torch.float32, device=num.device)
-                torch.autograd.backward(num, self._one)      # gradient exactly 1 (unit_grad), from a tensor that needs no fill
+                roots, seeds = [num], [self._one]            # gradient exactly 1 (unit_grad), from a tensor that needs no fill
             else:
                 num, den = weighted_nll_sums(logits, y, mask_from_draws(draws, p), self.class_weight)
-                num.backward()
+                roots, seeds = [num], [None]
+            if self.pos_losses:
+                # d + 0.1 c join the loss numerator (times the weight sum the CE kernel has just written: _back divides by it)
+                # and their gradient, pre-multiplied the same way, seeds the position stream's output
+                g_p = self._pos.run(self._pos_tables(g), pos_p, weight_sum=b.wsum_slot, loss_num=b.loss_slot)
+                roots.append(pos_p)
+                seeds.append(g_p)
+            torch.autograd.backward(roots, seeds)
             if queue is not None:
                 queue.flush()                # (inside the step's scale-pool window: its partial sums take no block, but stay in order)
             if side is not None:
@@ -483,9 +549,11 @@ class TrainStep:
                  "nesterov": False, "maximize": False, "foreach": None, "differentiable": False, "fused": None,
                  "params": list(range(len(b.params)))}
         ctr = getattr(self, "_seed_ctr", None)
-        return {"state": state, "param_groups": [group],
-                "spgnn": {"steps": b.steps, "seed_ctr": int(ctr.item()) if ctr is not None else 0,
-                          "generator": self.gen.get_state().clone(), "mask_seed": self._mask_seed}}
+        extra = {"steps": b.steps, "seed_ctr": int(ctr.item()) if ctr is not None else 0,
+                 "generator": self.gen.get_state().clone(), "mask_seed": self._mask_seed}
+        if self.pos_losses:
+            extra["pos_losses"] = self._pos.state_dict() if self._pos is not None else getattr(self, "_pos_pending", None)
+        return {"state": state, "param_groups": [group], "spgnn": extra}
 
     def load_state_dict(self, sd: dict) -> None:
         """Inverse of :meth:`state_dict`; also takes a plain ``torch.optim.SGD`` state dict (no ``"spgnn"`` entry: the
@@ -525,6 +593,12 @@ class TrainStep:
             ctr = getattr(self, "_seed_ctr", None)
             if ctr is not None:
                 ctr.fill_(int(extra["seed_ctr"]))
+            pos = extra.get("pos_losses")
+            if self.pos_losses and pos is not None:
+                if self._pos is not None:
+                    self._pos.load_state_dict(pos)
+                else:
+                    self._pos_pending = pos          # applied when the first step knows p's width
         # (steps == 0 with zeroed buffers is exact under a captured graph too: the kernel's first-step form equals
         # momentum * 0 + g)
 
