@@ -357,24 +357,29 @@ def gat_stack(sd, src, dst, n, fvs, prefix="gat_layers.", negative_slope=0.2, ac
     return F.normalize(out, p=2, dim=1) if norm else out
 
 
-def spgnn_pel_stack(sd, src, dst, n, fvs, pos_enc, negative_slope=0.2, activation=F.elu, p_activation=torch.tanh, drop=None):
+def spgnn_pel_stack(sd, src, dst, n, fvs, pos_enc, negative_slope=0.2, activation=F.elu, p_activation=torch.tanh, drop=None,
+                    residual=True):
     """reference models.py:472-484 (GATPSPGNN.forward).
     ``drop``: training mode with GIVEN masks - {("feat" | "attn", "s" | "p", layer): scaled multiplier} for the structure
     ("s": gat_layers) and position ("p": pgnn_layers) GATConv's ``feat_drop`` (N, F_in) and ``attn_drop`` (E, H); a missing
     key = that dropout is off (the reference builds layer 0 of both streams, the last position layer and the output layer
-    with rate 0: models.py:431-434, 449-456).  None: eval mode."""
+    with rate 0: models.py:431-434, 449-456).  None: eval mode.
+    ``residual``: the structure layers were built residual (every shipped config); the position layers always are
+    (models.py:442-455).  A residual layer without a ``res_fc.weight`` whose widths match carries DGL's identity residual
+    (e.g. a position layer as wide as the one before it)."""
     L = _count_layers(sd, "pgnn_layers.")
     d = drop or {}
     h_s, h_p = fvs, pos_enc
+
+    def layer(prefix, h, act, key, res):
+        return _gat_layer(sd, prefix, src, dst, n, h, negative_slope, act, residual_identity=_is_identity_res(sd, prefix, res),
+                          feat_keep=d.get(("feat",) + key), attn_keep=d.get(("attn",) + key))
     for l in range(L):
         h_s = torch.cat([h_s, h_p], dim=1)
-        h_s = _gat_layer(sd, f"gat_layers.{l}.", src, dst, n, h_s, negative_slope, activation,
-                         feat_keep=d.get(("feat", "s", l)), attn_keep=d.get(("attn", "s", l))).flatten(1)
-        h_p = _gat_layer(sd, f"pgnn_layers.{l}.", src, dst, n, h_p, negative_slope, p_activation,
-                         feat_keep=d.get(("feat", "p", l)), attn_keep=d.get(("attn", "p", l))).flatten(1)
+        h_s = layer(f"gat_layers.{l}.", h_s, activation, ("s", l), residual).flatten(1)
+        h_p = layer(f"pgnn_layers.{l}.", h_p, p_activation, ("p", l), True).flatten(1)
     h_s = torch.cat([h_s, h_p], dim=1)
-    h_s = _gat_layer(sd, f"gat_layers.{L}.", src, dst, n, h_s, negative_slope, activation,
-                     feat_keep=d.get(("feat", "s", L)), attn_keep=d.get(("attn", "s", L))).mean(1)
+    h_s = layer(f"gat_layers.{L}.", h_s, activation, ("s", L), residual).mean(1)
     return h_s, h_p
 
 

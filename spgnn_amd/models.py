@@ -358,15 +358,16 @@ class GATPSPGNN(_InferenceScoped, nn.Module):
         return plan
 
     def _lspe_ok(self, g, x: torch.Tensor, h_p: torch.Tensor) -> bool:
-        """The fused level needs two structure heads and one position head of the same width, Linear residuals and fusable
-        activations in every level (all reference configs), fp32 rows, and a graph the kernels take (ops.lspe_level_supported)."""
+        """The fused level needs two structure heads and one position head of the same width, a Linear residual on the structure
+        layer and a Linear or identity one (input as wide as its output) on the position layer, fusable activations in every
+        level (all reference configs), fp32 rows, and a graph the kernels take (ops.lspe_level_supported)."""
         from . import nn as _nn
         from .nn import Identity, _act_code
         if not (FUSE_LSPE and x.is_cuda and _nn.SCORES_FROM_FT and x.dtype == torch.float32):
             return False
         for s_layer, p_layer in zip(self.gat_layers[:-1], self.pgnn_layers):
             if not (s_layer._num_heads == 2 and p_layer._num_heads == 1 and s_layer._out_feats == p_layer._out_feats
-                    and isinstance(s_layer.res_fc, nn.Linear) and isinstance(p_layer.res_fc, nn.Linear)
+                    and isinstance(s_layer.res_fc, nn.Linear) and isinstance(p_layer.res_fc, (nn.Linear, Identity))
                     and _act_code(s_layer.activation) is not None and _act_code(p_layer.activation) is not None
                     and not isinstance(s_layer.res_fc, Identity)):
                 return False
@@ -379,9 +380,10 @@ class GATPSPGNN(_InferenceScoped, nn.Module):
         csc = g.csc(x.device)
         for l, (s_layer, p_layer) in enumerate(zip(self.gat_layers[:-1], self.pgnn_layers)):
             d = plan[l]
+            p_res = isinstance(p_layer.res_fc, nn.Linear)          # else an identity residual (_lspe_ok)
             w_s = ops.weight_cat(s_layer.fc.weight, s_layer.res_fc.weight, want_t=x.requires_grad)
-            w_p = ops.weight_cat(p_layer.fc.weight, p_layer.res_fc.weight, want_t=xp.requires_grad)
-            cfg = {"res_s": True, "res_p": True, "act": (_act_code(s_layer.activation), _act_code(p_layer.activation)),
+            w_p = ops.weight_cat(p_layer.fc.weight, p_layer.res_fc.weight if p_res else None, want_t=xp.requires_grad)
+            cfg = {"res_s": "linear", "res_p": "linear" if p_res else "identity", "act": (_act_code(s_layer.activation), _act_code(p_layer.activation)),
                    "slope": (float(s_layer.negative_slope), float(p_layer.negative_slope)), "p_attn": (d["ps"], d["pp"]),
                    "seed_attn": (d["seed_s"], d["seed_p"]), "fp": d["fp"], "fseed": d["fseed"], "fp2": d["fp2"], "fseed2": d["fseed2"]}
             x, xp = ops.lspe_level(csc, x, xp, w_s, w_p, (s_layer.attn_l, s_layer.attn_r), (p_layer.attn_l, p_layer.attn_r),

@@ -2211,11 +2211,20 @@ class _LspeLevelFn(torch.autograd.Function):
     GEMMs' epilogues, aggregated by ONE traversal of the graph (spgnn_lspe_fwd) that writes the next level's two inputs:
     buf (N, 3D) = [h_s' | h_p'] under the next structure layer's feature dropout and xp (N, D) = h_p' under the next position
     layer's.  Backward: spgnn_lspe_bwd_dst + spgnn_lspe_bwd_src straight into the GEMM-gradient buffers of both layers, then
-    their weight / input gradient products."""
+    their weight / input gradient products.
+
+    Residuals (cfg ``res_s`` / ``res_p``): "linear" - W_res is the second half of the layer's weight_cat operand and the residual
+    rows are the second half of its projection; "identity" (the position layer only, when its input is as wide as its output:
+    DGL's GATConv then adds the input itself) - ``w_p`` is W_fc alone, the kernels read the residual rows from x_p, and the
+    input gradient takes g_pre in the epilogue of its product."""
 
     @staticmethod
     def forward(ctx, x_s, x_p, w_s, w_p, al_s, ar_s, al_p, ar_p, bias_s, bias_p, csc: DeviceCSC, D: int, cfg: dict):
         ctx.set_materialize_grads(False)
+        if cfg["res_s"] != "linear" or cfg["res_p"] not in ("linear", "identity"):
+            raise ValueError(f"lspe_level: residuals {cfg['res_s']!r} / {cfg['res_p']!r} (structure: linear; position: linear or identity)")
+        if cfg["res_p"] == "identity" and not (x_p.shape[1] == D and _rows_aligned(x_p)):
+            raise ValueError(f"lspe_level: an identity residual needs x_p (N, {D}) with 16-byte rows, got {tuple(x_p.shape)}")
         N = x_s.shape[0]
         E = csc.num_edges
         dev = x_s.device
@@ -2240,11 +2249,11 @@ class _LspeLevelFn(torch.autograd.Function):
         attn = [torch.empty((E, 2), dtype=torch.float32, device=dev), torch.empty((E, 1), dtype=torch.float32, device=dev)]
         nbr8 = csc.ell()[0]
         G = (_capi.LspeFwdGroup * 2)()
-        for i, (H, has_res, bias) in enumerate(((2, cfg["res_s"], bias_s), (1, cfg["res_p"], bias_p))):
+        for i, (H, res, x, bias) in enumerate(((2, cfg["res_s"], x_s, bias_s), (1, cfg["res_p"], x_p, bias_p))):
             y, s_ = ys[i], ss[i]
             g = G[i]
             g.ft, g.ft_stride = y.data_ptr(), y.stride(0)
-            g.res, g.res_stride = (y[:, H * D:].data_ptr(), y.stride(0)) if has_res else (0, 0)
+            g.res, g.res_stride = (y[:, H * D:].data_ptr(), y.stride(0)) if res == "linear" else (x.data_ptr(), x.stride(0))
             g.bias = _ptr(bias)
             g.el, g.er, g.s_stride = s_.data_ptr(), s_[:, H:].data_ptr(), s_.stride(0)
             g.attn = attn[i].data_ptr()
@@ -2282,7 +2291,8 @@ class _LspeLevelFn(torch.autograd.Function):
                 g_xp = g_xp.contiguous()
         xs, ws, ys, ss, attns = (x_s, x_p), (w_s, w_p), (y_s, y_p), (s_s, s_p), (attn_s, attn_p)
         vecs, scl = ((al_s, ar_s), (al_p, ar_p)), ((sx_s, sw_s), (sx_p, sw_p))
-        Hs, res = (2, 1), (cfg["res_s"], cfg["res_p"])
+        Hs = (2, 1)
+        res = (True, cfg["res_p"] == "linear")            # else the position layer's identity residual
         g_y = [torch.empty_like(y) for y in ys]
         g_s = [torch.empty_like(s_) for s_ in ss]
         g_e = [torch.empty((E, H), dtype=torch.float32, device=dev) for H in Hs]
@@ -2296,7 +2306,8 @@ class _LspeLevelFn(torch.autograd.Function):
             d.ft, d.ft_stride = ys[i].data_ptr(), ys[i].stride(0)
             d.el, d.er, d.s_stride, d.attn = ss[i].data_ptr(), ss[i][:, H:].data_ptr(), ss[i].stride(0), attns[i].data_ptr()
             d.g_pre, d.g_pre_stride = g_pre[i].data_ptr(), g_pre[i].stride(0)
-            d.g_e, d.g_er, d.gs_stride, d.absmax = g_e[i].data_ptr(), g_s[i][:, H:].data_ptr(), g_s[i].stride(0), amax[i].data_ptr()
+            # (g_pre is part of the products' operand [g_ft | g_pre] only with a linear residual: else its maxima stay out of the scale)
+            d.g_e, d.g_er, d.gs_stride, d.absmax = g_e[i].data_ptr(), g_s[i][:, H:].data_ptr(), g_s[i].stride(0), amax[i].data_ptr() if res[i] else 0
             d.H, d.act, d.slope, d.p_drop, d.seed = H, cfg["act"][i], cfg["slope"][i], cfg["p_attn"][i], cfg["seed_attn"][i]
             q.attn, q.g_e, q.g_pre, q.g_pre_stride = attns[i].data_ptr(), g_e[i].data_ptr(), g_pre[i].data_ptr(), g_pre[i].stride(0)
             q.g_ft, q.g_ft_stride = g_y[i].data_ptr(), g_y[i].stride(0)
@@ -2336,10 +2347,11 @@ class _LspeLevelFn(torch.autograd.Function):
             if ctx.needs_input_grad[i]:
                 gx = torch.empty((N, (K + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :K]
                 w_t, w_t_ps = ctx.wts[i]
+                add = None if res[i] else g_pre[i]           # identity residual: g_x = g_ft W_fc + g_pre
                 if w_t_ps is not None:
-                    nt[i] = NtProblem(g_y[i], w_t_ps, sg, sw, out=gx, b_presplit=True)
+                    nt[i] = NtProblem(g_y[i], w_t_ps, sg, sw, out=gx, b_presplit=True, addend=add)
                 else:
-                    nt[i] = NtProblem(g_y[i], w_t if w_t is not None else ws[i].t().contiguous(), sg, sw, out=gx)
+                    nt[i] = NtProblem(g_y[i], w_t if w_t is not None else ws[i].t().contiguous(), sg, sw, out=gx, addend=add)
                 grads_x[i] = gx
         def input_gradients():
             if nt[0] is not None and nt[1] is not None:
@@ -3339,7 +3351,8 @@ class NtProblem:
     """One gemm_nt call, described but not launched (see :func:`gemm_nt_pair`); ``out`` is allocated here."""
 
     def __init__(self, a, b, scale_a=None, scale_b=None, out=None, score_l=None, score_r=None, score_out=None, b_presplit=False,
-                 a_presplit=False):
+                 a_presplit=False, addend=None):
+        """``addend`` (M, N), 16-byte rows: out = a @ b^T + addend, added in the epilogue."""
         _require_cuda(a, b)
         M, K = a.shape
         N = b.shape[0]
@@ -3357,9 +3370,19 @@ class NtProblem:
         q.scale_a, q.scale_b = _ptr(scale_a), _ptr(scale_b)
         q.score_l, q.score_r, q.score_out = _ptr(score_l), _ptr(score_r), _ptr(score_out)
         q.score_cols = score_l.numel() if score_out is not None else 0
+        self.addend = addend
+        if addend is not None:
+            assert addend.shape == (M, N) and _rows_aligned(addend)
+            q.addend, q.addend_stride = addend.data_ptr(), addend.stride(0)
 
     def run(self) -> torch.Tensor:
-        return gemm_nt(self.a, self.b, **self.kw)
+        if self.addend is None:
+            return gemm_nt(self.a, self.b, **self.kw)
+        import ctypes
+        with torch.cuda.device(self.a.device), _timed("gemm_nt", self.shape):
+            _capi.check(_capi.load().spgnn_gemm_nt_problem_run(ctypes.byref(self.c), self.b_presplit, _stream(self.a)),
+                        "spgnn_gemm_nt_problem_run")
+        return self.out
 
 
 def gemm_nt_pair(first: NtProblem, second: NtProblem):

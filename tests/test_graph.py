@@ -154,3 +154,32 @@ def test_tree_downstream_graph_mode_follows_the_reference_rule():
         G.edges_from_adj(np.eye(3), graph_mode="upstream")
     g = G.graph_from_adj(synthetic.random_tree_adj(20, rng), graph_mode="tree_downstream")
     assert g.number_of_edges() == 39
+
+
+def test_degree_edge_batch_layout():
+    """tests/util.DEGREE_EDGE_TREES (the fused SPGNN level's degree edges, test_hip_lspe.py): the degrees the builder promises
+    are the graph's, in both directions, with the statistics the host checks before it picks the fused kernels; every degree
+    1..8 occurs; degree 1 sits next to degree 8 inside one wave of 16- and of 32-lane teams (4 and 2 nodes per wave), a 16-lane
+    wave holds four different degrees, and N leaves a partial last block (16, 8 or 4 nodes per block)."""
+    from tests.util import DEGREE_EDGE_TREES, degree_edge_batch, exact_degrees, tree_adj_from_child_counts
+    adjs, deg = degree_edge_batch()
+    g = G.batch([G.graph_from_adj(a) for a in adjs])
+    N = g.number_of_nodes()
+    assert N == deg.shape[0] and N % 16 != 0
+    csc = g.csc()
+    assert np.array_equal((csc.indptr[1:] - csc.indptr[:-1]).numpy(), deg)
+    assert np.array_equal((csc.out_indptr[1:] - csc.out_indptr[:-1]).numpy(), deg)
+    assert (csc.min_in_degree, csc.max_in_degree, csc.min_out_degree, csc.max_out_degree) == (1, 8, 1, 8)
+    assert set(deg.tolist()) == set(range(1, 9))
+    for per in (4, 2):
+        waves = [set(deg[i:i + per].tolist()) for i in range(0, N, per)]
+        assert any({1, 8} <= w for w in waves), per
+    assert any(len(set(deg[i:i + 4].tolist())) == 4 for i in range(0, N, 4))
+    for c in DEGREE_EDGE_TREES:                    # each tree: a tree (n - 1 undirected edges, connected) of the promised degrees
+        a = tree_adj_from_child_counts(c)
+        n = a.shape[0]
+        assert np.array_equal(a, a.T) and np.all(np.diag(a) == 1) and (a.sum() - n) == 2 * (n - 1)
+        assert np.array_equal(a.sum(0), exact_degrees(c))
+        assert nx.is_connected(nx.from_numpy_array(a))
+    with pytest.raises(ValueError):
+        tree_adj_from_child_counts([1, 0, 2])      # node 2 is never reached

@@ -11,7 +11,7 @@ from oracle import dgl_cpu as O
 from spgnn_amd import models, synthetic
 from spgnn_amd.configs import class_weight_list, get_config
 from spgnn_amd.train import masked_weighted_ce
-from tests.util import mixed_err, rel_err
+from tests.util import mixed_err, rel_err, spgnn_host_masks
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -281,39 +281,6 @@ def test_loss_and_gradients_match_the_oracle_at_512_trees():
     assert e_loss < TOL
 
 
-def _spgnn_host_masks(plan, model, g):
-    """The dropout multipliers of ONE training-mode forward of GATPSPGNN, rebuilt on the host from the forward's own seed plan
-    (spgnn_amd.models.GATPSPGNN._seed_plan: per level the next structure layer's feature dropout over cat[h_s, h_p], the
-    structure / position layer's attention dropout, the next position layer's feature dropout) with the bit-exact host
-    copies of the kernels' counter hashes (tests/util.py) - in the oracle's layout: {(kind, stream, layer): multiplier}."""
-    import numpy as np
-
-    from tests.util import keep4_scale_host, keep_scale_host
-    csc = g.csc()
-    N, E = g.number_of_nodes(), csc.num_edges
-    eid = csc.eid.cpu().numpy()
-    head = model.gat
-    drop = {}
-
-    def attn(seed, H, p):
-        slot = keep_scale_host(seed, np.arange(E * H), p).reshape(E, H)          # CSC slot order -> edge-id order
-        edge = np.empty_like(slot)
-        edge[eid] = slot
-        return torch.from_numpy(edge)
-    for l, d in enumerate(plan):
-        s_layer, p_layer = head.gat_layers[l], head.pgnn_layers[l]
-        w_s, w_p = s_layer._num_heads * s_layer._out_feats, p_layer._num_heads * p_layer._out_feats
-        if d["fp"] > 0:
-            drop[("feat", "s", l + 1)] = torch.from_numpy(keep4_scale_host(d["fseed"], N, (w_s, w_p), d["fp"]))
-        if d["ps"] > 0:
-            drop[("attn", "s", l)] = attn(d["seed_s"], s_layer._num_heads, d["ps"])
-        if d["pp"] > 0:
-            drop[("attn", "p", l)] = attn(d["seed_p"], p_layer._num_heads, d["pp"])
-        if d["fp2"] > 0:
-            drop[("feat", "p", l + 1)] = torch.from_numpy(keep4_scale_host(d["fseed2"], N, (w_p,), d["fp2"]))
-    return drop
-
-
 @pytest.mark.parametrize("trees", [3, 64])
 def test_training_mode_step_with_dropout_on_matches_the_oracle(trees):
     """the TIMED workload's arithmetic - st_pgat_spgnn_3 in TRAINING mode, feature and attention dropout
@@ -342,7 +309,7 @@ def test_training_mode_step_with_dropout_on_matches_the_oracle(trees):
     plan = plans[0]
     rates = [(d["fp"], d["ps"], d["pp"], d["fp2"]) for d in plan]
     assert rates == [(0.1, 0.0, 0.0, 0.1), (0.1, 0.1, 0.1, 0.0), (0.0, 0.1, 0.0, 0.0)], rates     # the reference's placement
-    drop = _spgnn_host_masks(plan, model, g)
+    drop = spgnn_host_masks(plan, model, g)
     assert sorted(drop) == [("attn", "p", 1), ("attn", "s", 1), ("attn", "s", 2), ("feat", "p", 1), ("feat", "s", 1), ("feat", "s", 2)]
     for k, m in drop.items():
         kept = float((m > 0).float().mean())
