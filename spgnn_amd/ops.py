@@ -1896,7 +1896,9 @@ class _GATLayerFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)       # no zero tensor for the unused gradient of `attn`
         HD = H * D
         x = _rowmajor(x)
-        split = GEMM_MODE == "f16x3" and _rows_aligned(x) and _rows_aligned(w_cat) and x.shape[0] > 0
+        # the backward's input-gradient product takes g_y = [g_ft | g_pre] (N, HD [+HD]) as its row operand: 16-byte rows too
+        split = (GEMM_MODE == "f16x3" and _rows_aligned(x) and _rows_aligned(w_cat) and w_cat.shape[0] % 4 == 0
+                 and x.shape[0] > 0)
         if split:                                      # (N, HD [+HD]) = [ft | res] on the fp16 matrix cores
             s, sx = scores_fwd(x, w_lr, want_scale=True)   # (N, 2H) = [el | er]; the scale of x comes for free
             sw = operand_scale(w_cat)                      # attached by weight_cat, else one absmax pass

@@ -183,3 +183,67 @@ def test_degree_edge_batch_layout():
         assert nx.is_connected(nx.from_numpy_array(a))
     with pytest.raises(ValueError):
         tree_adj_from_child_counts([1, 0, 2])      # node 2 is never reached
+    # past the fast path (test_hip_degree_edges.py): degrees 9 and 10 in both directions, in a 16-lane wave and a 32-lane wave
+    # with degree 1, and in a 16-lane wave with degree 8
+    from tests.util import PAST_FAST_PATH_TREES, past_fast_path_batch, star_edges, zero_in_degree_edges
+    adjs, deg = past_fast_path_batch()
+    g = G.batch([G.graph_from_adj(a) for a in adjs])
+    N = g.number_of_nodes()
+    csc = g.csc()
+    assert N == deg.shape[0] and N % 16 != 0
+    assert np.array_equal((csc.indptr[1:] - csc.indptr[:-1]).numpy(), deg)
+    assert np.array_equal((csc.out_indptr[1:] - csc.out_indptr[:-1]).numpy(), deg)
+    assert (csc.min_in_degree, csc.max_in_degree, csc.min_out_degree, csc.max_out_degree) == (1, 10, 1, 10)
+    assert {1, 2, 8, 9, 10} <= set(deg.tolist())
+    assert any({1, 10} <= set(deg[i:i + 2].tolist()) for i in range(0, N, 2))
+    assert any({1, 8, 10} <= set(deg[i:i + 4].tolist()) for i in range(0, N, 4))
+    assert any({8, 9} <= set(deg[i:i + 4].tolist()) for i in range(0, N, 4))
+    for c in PAST_FAST_PATH_TREES:
+        a = tree_adj_from_child_counts(c)
+        assert np.array_equal(a.sum(0), exact_degrees(c)) and nx.is_connected(nx.from_numpy_array(a))
+    # zero in-degree (not a tree): in-degrees 0..9, zero-degree nodes beside degree-9 ones, the last node isolated
+    s, d, n = zero_in_degree_edges()
+    csc = G.TreeGraph((s, d), n).csc()
+    ind = (csc.indptr[1:] - csc.indptr[:-1]).numpy()
+    outd = (csc.out_indptr[1:] - csc.out_indptr[:-1]).numpy()
+    assert set(ind.tolist()) == set(range(10)) and ind[-1] == 0 and outd[-1] == 0 and (outd == 0).sum() == 1
+    assert any(ind[i] == 9 and ind[i + 1] == 0 for i in range(n - 1))
+    assert csc.min_in_degree == 0 and csc.max_in_degree == 9
+    # stars on either side of the one-byte argmax limit (in-degree <= 254)
+    for k, root in ((253, 254), (254, 255)):
+        s, d, n = star_edges(k)
+        csc = G.TreeGraph((s, d), n).csc()
+        ind = (csc.indptr[1:] - csc.indptr[:-1]).numpy()
+        assert ind[0] == root and csc.max_in_degree == root and csc.max_out_degree == root and (ind[1:] == 2).all()
+
+
+def test_gat_geometry_rule_covers_every_instance(lib):
+    """tests/util.pick_gat restates the vector GAT kernels' geometry rule (spgnn_rows.h pick_team, spgnn_kernels.hip pick_gat):
+    it agrees with the library's host queries over a grid of shapes, every instance it reaches is a case of SPGNN_FOR_R_CH (teams
+    narrower than a wave only with R <= 4: launch_small_team has no other instances), and the row-kernel shapes of
+    test_hip_degree_edges.py select every instance plus the scalar fallback.  A change to the dispatch fails here rather than
+    leaving an instance untested."""
+    import os
+    import re
+    from tests.util import GAT_INSTANCE_SHAPES, pick_gat, pick_team
+    src = open(os.path.join(os.path.dirname(G.__file__), "csrc", "spgnn_kernels.hip")).read()
+    macro = src[src.index("#define SPGNN_FOR_R_CH"):]
+    macro = macro[:macro.index("default:")]
+    cases = {(int(a), int(b)) for a, b in re.findall(r"X\((\d+), (\d+)\)", macro)}
+    assert len(cases) == 14
+    reached = set()
+    for H in range(1, 17):
+        for D in range(1, 2049):
+            inst = pick_gat(H, D)
+            assert bool(lib.spgnn_gat_can_fuse_mean(H, D)) == (inst is not None and inst[2] >= 1), (H, D)
+            if inst is not None:
+                T, R, CH = inst
+                assert (R, CH) in cases and T in (16, 32, 64) and (T == 64 or R <= 4), (H, D, inst)
+                assert H * D == 4 * T * R
+                reached.add(inst)
+    for F_ in range(1, 2049):
+        assert bool(lib.spgnn_spmm_max_u8_supported(F_)) == (pick_team(F_, True) is not None), F_
+    assert {(R, CH) for _, R, CH in reached} == cases                       # no dead case in the switch
+    tested = [pick_gat(H, D) for H, D in GAT_INSTANCE_SHAPES]
+    assert set(tested) - {None} == reached and None in tested, sorted(reached - set(tested))
+    assert len(reached) == 20

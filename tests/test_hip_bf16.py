@@ -21,6 +21,7 @@ from spgnn_amd import models, nn as snn, ops, ops_bf16, synthetic
 from spgnn_amd.configs import class_weight_list, get_config
 from spgnn_amd.graph import TreeGraph
 from spgnn_amd.train import TrainStep, masked_weighted_ce
+from tests.util import close_to_model as _close_to_model
 from tests.util import rel_err, tree_batch_edges
 
 pytestmark = pytest.mark.gpu
@@ -191,17 +192,6 @@ def test_cat_dropout_bf16_matches_fp32_mask():
 # ----------------------------------------------------------------------------------------------------------------
 # GATConv layer: HIP bf16 path vs the storage model (fp64 arithmetic, bf16 rounding at the storage points)
 # ----------------------------------------------------------------------------------------------------------------
-def _close_to_model(x, ref, what, frac=0.02):
-    """x (HIP) against the storage model: normwise within one bf16 ulp, and all but a small fraction of the elements
-    within fp32-accumulation noise of the model (the rest crossed a bf16 rounding boundary somewhere upstream)."""
-    x, ref = x.detach().float().cpu().double(), ref.detach().double().cpu()
-    scale = ref.abs().max().item() or 1.0
-    d = (x - ref).abs()
-    assert d.max().item() <= 2 * ULP * scale, (what, d.max().item() / scale)
-    off = (d > 1e-4 * scale).double().mean().item()
-    assert off <= frac, (what, off)
-
-
 @pytest.mark.parametrize("F_in,H,D,res,act,mean", [(128, 2, 64, True, "elu", False), (256, 2, 128, True, "elu", False),
                                                    (64, 1, 64, False, None, False), (128, 2, 1024, True, None, True),
                                                    (64, 4, 128, False, None, True), (200, 2, 512, True, None, True),

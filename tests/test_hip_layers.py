@@ -11,6 +11,7 @@ from spgnn_amd import nn as snn
 from spgnn_amd import ops
 from spgnn_amd.graph import TreeGraph
 from tests.util import keep4_scale_host, keep_scale_host, rel_err, tree_batch_edges
+from tests.util import oracle_gat as _oracle_gat
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 1e-5, 5e-5
@@ -19,15 +20,6 @@ FWD_TOL, GRAD_TOL = 1e-5, 5e-5
 def _graph(ns, seed=0):
     s, d, n = tree_batch_edges(ns, seed)
     return TreeGraph((s, d), n).to("cuda"), torch.from_numpy(s), torch.from_numpy(d), n
-
-
-def _oracle_gat(layer, src, dst, n, x, act, dtype=torch.float32, attn_keep=None):
-    sd = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in layer.state_dict().items()}
-    xo = x.detach().cpu().to(dtype).requires_grad_(True)
-    rst, a = O.gat_conv(src, dst, n, xo, sd["fc.weight"], sd["attn_l"], sd["attn_r"], sd.get("res_fc.weight"),
-                        sd.get("bias"), layer.negative_slope, act, attn_keep,
-                        residual_identity=isinstance(layer.res_fc, snn.Identity))
-    return rst, a, xo, sd
 
 
 # every GATConv shape of the configs + head sweep + odd shapes (scalar fallback)

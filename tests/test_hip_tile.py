@@ -10,6 +10,8 @@ import torch
 
 from spgnn_amd import _capi, ops, ops_bf16, synthetic
 from spgnn_amd.graph import TreeGraph
+from tests.util import gat_raw_inputs as _inputs
+from tests.util import run_gat_raw_fp32 as _run_fp32
 from tests.util import rel_err, tree_batch_edges
 
 pytestmark = pytest.mark.gpu
@@ -21,35 +23,6 @@ def _graph(ns, seed=0):
     g.batch_num_nodes_list = list(ns)
     g.batch_num_edges_list = [3 * k - 2 for k in ns]
     return g.to("cuda"), n
-
-
-def _inputs(n, H, D, dtype, seed):
-    gen = torch.Generator(device="cuda").manual_seed(seed)
-    y = (torch.randn(n, 2 * H * D, device="cuda", generator=gen)).to(dtype)          # [ft | res]
-    s = torch.randn(n, 2 * H, device="cuda", generator=gen)
-    bias = torch.randn(H * D, device="cuda", generator=gen) * 0.1
-    g_out = torch.randn(n, H * D, device="cuda", generator=gen).to(dtype)
-    return y, s, bias, g_out
-
-
-def _run_fp32(csc, y, s, bias, g_out, H, D, act, p, od, score):
-    HD = H * D
-    ft, res = y[:, :HD], y[:, HD:]
-    total = HD + 8
-    buf = torch.zeros(y.shape[0], total, device="cuda")
-    out_drop = (od, 77, total, 4) if od > 0 else None
-    out_view = buf[:, 4:4 + HD] if od > 0 else None
-    blk = ops.new_scale_block("cuda")
-    out, _, attn = ops.gat_fwd_raw(csc, ft, s[:, :H], s[:, H:], res, bias, H, D, 0.2, act, p, 1234, out=out_view, out_drop=out_drop,
-                                   out_absmax=blk)
-    g_y = torch.zeros_like(y)
-    g_s = torch.zeros_like(s)
-    blk2 = ops.new_scale_block("cuda")
-    al = torch.randn(HD, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3)) if score else None
-    ar = torch.randn(HD, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4)) if score else None
-    g_e = ops.gat_bwd_raw(csc, ft, s[:, :H], s[:, H:], attn, g_out, out if act != ops.ACT_NONE else None, H, D, 0.2, act, p, 1234,
-                          g_y[:, HD:], g_y[:, :HD], g_s[:, :H], g_s[:, H:], absmax=blk2, score_l=al, score_r=ar, out_drop=out_drop)
-    return dict(out=out.clone(), attn=attn, g_y=g_y, g_s=g_s, g_e=g_e, blk=blk.clone(), blk2=blk2.clone())
 
 
 @pytest.mark.parametrize("H,D", [(2, 64), (2, 128), (1, 64), (1, 128), (4, 64)])

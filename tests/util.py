@@ -173,3 +173,146 @@ def degree_edge_batch():
     """-> (list of adjs, per-node degrees) of DEGREE_EDGE_TREES, batched in order."""
     adjs = [tree_adj_from_child_counts(c) for c in DEGREE_EDGE_TREES]
     return adjs, np.concatenate([exact_degrees(c) for c in DEGREE_EDGE_TREES])
+
+
+# Batched trees just past the 8-slot fast path of the traversal kernels (kMaxFast, spgnn_rows.h): in- and out-degrees 9 and 10
+# (the general CSC walk) next to degree 8 and degree 1 (the fast path) in the same wave, see
+# test_graph.test_past_the_fast_path_batch_layout.
+PAST_FAST_PATH_TREES = (
+    [8, 7, 6, 8, 0, 2],                         # root 9; children of degree 9, 8, 10, 2, 4
+    [],                                         # id 32: a one-node tree (degree 1) beside the next root (degree 10) ...
+    [9] + [6, 8, 7, 0] + [0] * 5 + [1],         # ... then 8, 10, 9, 2: a 16-lane wave of degrees 1, 10, 8, 10
+    [6, 7],                                     # degree 7 root beside a degree 9 child
+    [],
+    [7] + [6] * 7,                              # degree 8 throughout
+    [],
+)
+
+
+def past_fast_path_batch():
+    """-> (list of adjs, per-node degrees) of PAST_FAST_PATH_TREES, batched in order."""
+    adjs = [tree_adj_from_child_counts(c) for c in PAST_FAST_PATH_TREES]
+    return adjs, np.concatenate([exact_degrees(c) for c in PAST_FAST_PATH_TREES])
+
+
+def zero_in_degree_edges():
+    """(src, dst, n) of a directed graph that is not a tree: nodes without in-edges (among them the last node, whose padded
+    neighbour row the host builder clamps to the last edge) and without out-edges, next to nodes of in-degree 1..9."""
+    n = 40
+    src, dst = [], []
+    for v in range(n - 1):
+        k = v % 11 - 1                                  # in-degree -1 -> 0, then 0..9 (no self loops)
+        for j in range(max(k, 0)):
+            src.append((v + 3 + 5 * j) % (n - 1)); dst.append(v)
+    return np.array(src, np.int64), np.array(dst, np.int64), n
+
+
+def star_edges(k: int):
+    """(src, dst, n) of a star with k children, self loops included: the root's in- and out-degree is k + 1."""
+    s = np.concatenate([np.zeros(k, np.int64), np.arange(1, k + 1), np.arange(k + 1)])
+    d = np.concatenate([np.arange(1, k + 1), np.zeros(k, np.int64), np.arange(k + 1)])
+    return s, d, k + 1
+
+
+def oracle_gat(layer, src, dst, n, x, act, dtype=torch.float32, attn_keep=None):
+    """The oracle's GATConv (oracle.dgl_cpu.gat_conv) on a copy of ``layer``'s parameters and ``x`` in ``dtype``, as leaves:
+    -> (rst (N, H, D), a (E, H) per edge id, x leaf, {name: parameter leaf})."""
+    from oracle import dgl_cpu as O
+    from spgnn_amd import nn as snn
+    sd = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in layer.state_dict().items()}
+    xo = x.detach().cpu().to(dtype).requires_grad_(True)
+    rst, a = O.gat_conv(src, dst, n, xo, sd["fc.weight"], sd["attn_l"], sd["attn_r"], sd.get("res_fc.weight"),
+                        sd.get("bias"), layer.negative_slope, act, attn_keep,
+                        residual_identity=isinstance(layer.res_fc, snn.Identity))
+    return rst, a, xo, sd
+
+
+BF16_ULP = 2.0 ** -8       # bf16: 8 significant bits, round to nearest: relative rounding error <= 2^-9, one ulp = 2^-8
+
+
+def close_to_model(x, ref, what, frac=0.02):
+    """x (HIP, bf16 storage) against the bf16 storage model (oracle.dgl_cpu.Bf16Storage): normwise within two bf16 ulp, and all
+    but a small fraction of the elements within fp32-accumulation noise of the model (the rest crossed a bf16 rounding
+    boundary somewhere upstream).  -> the normwise error max|x - ref| / max|ref|."""
+    x, ref = x.detach().float().cpu().double(), ref.detach().double().cpu()
+    scale = ref.abs().max().item() or 1.0
+    d = (x - ref).abs()
+    assert d.max().item() <= 2 * BF16_ULP * scale, (what, d.max().item() / scale)
+    off = (d > 1e-4 * scale).double().mean().item()
+    assert off <= frac, (what, off)
+    return d.max().item() / scale
+
+
+# Python restatement of the vector GAT kernels' geometry rule (spgnn_rows.h pick_team, spgnn_kernels.hip pick_gat): an (H, D)
+# layer runs the instance (T lanes per node, R float4 chunks per lane, CH chunks per head; CH = 0: heads narrower than the
+# team), or None: the scalar fallback.  test_graph.test_gat_geometry_rule_covers_every_instance keeps it equal to the library.
+def pick_team(width: int, narrow: bool = False):
+    if width <= 0 or width & 3:
+        return None
+    q = width >> 2
+    if narrow and q <= 64 and q % 16 == 0 and q // 16 in (1, 2, 4):
+        return 16, q // 16
+    for t in (64, 32, 16):
+        if q % t == 0 and q // t in (1, 2, 4, 8):
+            return t, q // t
+    return None
+
+
+def pick_gat(H: int, D: int):
+    if D % 4:
+        return None
+    tr = pick_team(H * D, H in (1, 2))
+    if tr is None:
+        return None
+    T, R = tr
+    if D % (4 * T) == 0:
+        CH = D // (4 * T)
+        return (T, R, CH) if CH in (1, 2, 4, 8) and R % CH == 0 else None
+    if (4 * T) % D == 0 and ((D // 4) & (D // 4 - 1)) == 0:
+        return T, R, 0
+    return None
+
+
+# One (H, D) per vector GAT instance (the narrowest layer that selects it), plus a scalar-fallback shape last: the geometries of
+# the row-kernel tests in test_hip_degree_edges.py.
+GAT_INSTANCE_SHAPES = (
+    (2, 32), (1, 64), (2, 64), (1, 128), (2, 128), (1, 256),          # 16-lane teams: (16, 1, 0) .. (16, 4, 4)
+    (4, 32),                                                           # (32, 1, 0)
+    (4, 64), (4, 128), (2, 256), (1, 512),                             # (64, 1, 0) (64, 2, 0..2)
+    (8, 128), (4, 256), (2, 512), (1, 1024),                           # (64, 4, 0..4)
+    (16, 128), (8, 256), (4, 512), (2, 1024), (1, 2048),               # (64, 8, 0..8)
+    (3, 5),                                                            # scalar fallback
+)
+
+
+def gat_raw_inputs(n, H, D, dtype, seed):
+    """Random [ft | res] rows (dtype), scores [el | er], bias and output gradient of an (H, D) GATConv traversal."""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    y = (torch.randn(n, 2 * H * D, device="cuda", generator=gen)).to(dtype)          # [ft | res]
+    s = torch.randn(n, 2 * H, device="cuda", generator=gen)
+    bias = torch.randn(H * D, device="cuda", generator=gen) * 0.1
+    g_out = torch.randn(n, H * D, device="cuda", generator=gen).to(dtype)
+    return y, s, bias, g_out
+
+
+def run_gat_raw_fp32(csc, y, s, bias, g_out, H, D, act, p, od, score):
+    """One forward + backward of the fp32 GAT traversals through ops.gat_fwd_raw / gat_bwd_raw (row or tile kernels, whatever
+    ops.tile_plan picks): attention dropout p, the consumer's output dropout od, the score term with ``score``."""
+    from spgnn_amd import ops
+    HD = H * D
+    ft, res = y[:, :HD], y[:, HD:]
+    total = HD + 8
+    buf = torch.zeros(y.shape[0], total, device="cuda")
+    out_drop = (od, 77, total, 4) if od > 0 else None
+    out_view = buf[:, 4:4 + HD] if od > 0 else None
+    blk = ops.new_scale_block("cuda")
+    out, _, attn = ops.gat_fwd_raw(csc, ft, s[:, :H], s[:, H:], res, bias, H, D, 0.2, act, p, 1234, out=out_view, out_drop=out_drop,
+                                   out_absmax=blk)
+    g_y = torch.zeros_like(y)
+    g_s = torch.zeros_like(s)
+    blk2 = ops.new_scale_block("cuda")
+    al = torch.randn(HD, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3)) if score else None
+    ar = torch.randn(HD, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4)) if score else None
+    g_e = ops.gat_bwd_raw(csc, ft, s[:, :H], s[:, H:], attn, g_out, out if act != ops.ACT_NONE else None, H, D, 0.2, act, p, 1234,
+                          g_y[:, HD:], g_y[:, :HD], g_s[:, :H], g_s[:, H:], absmax=blk2, score_l=al, score_r=ar, out_drop=out_drop)
+    return dict(out=out.clone(), attn=attn, g_y=g_y, g_s=g_s, g_e=g_e, blk=blk.clone(), blk2=blk2.clone())
