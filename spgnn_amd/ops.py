@@ -2816,9 +2816,10 @@ def linear_mean_fold_buffers(w_fc, w_res, bias, w_cls, b_cls, H: int, D: int, bf
     blk = None if bf16 else new_scale_block(dev)
     ws = _FOLD_WS.get((str(dev), H, F_))
     if ws is None:                                          # persistent scratch: partial sums and the (self re-arming) tickets
+        # both sized for the wider column layout (the x block present): the entry serves x_block 0 and 1 alike
         n = int(_capi.load().spgnn_linear_mean_fold_workspace(H, F_))
         ws = _FOLD_WS[(str(dev), H, F_)] = (torch.empty((n,), dtype=torch.float32, device=dev),
-                                            torch.zeros((Kp // 32 + 2,), dtype=torch.int32, device=dev))
+                                            torch.zeros((_pad16((H + 1) * F_) // 32 + 2,), dtype=torch.int32, device=dev))
     wf = w_fc if w_fc.stride(1) == 1 else w_fc.contiguous()
     wr = None if w_res is None else (w_res if w_res.stride(1) == 1 else w_res.contiguous())
     wc = w_cls if w_cls.stride(1) == 1 else w_cls.contiguous()

@@ -1,6 +1,8 @@
 """Host-side graph construction and positional encoding: bit-exact against the networkx
 restatement of the reference's rule (oracle/graph_rule_nx.py; reference job_runner.py:1319-1344,
 1712-1801, 1882)."""
+import re
+
 import networkx as nx
 import numpy as np
 import pytest
@@ -247,3 +249,47 @@ def test_gat_geometry_rule_covers_every_instance(lib):
     tested = [pick_gat(H, D) for H, D in GAT_INSTANCE_SHAPES]
     assert set(tested) - {None} == reached and None in tested, sorted(reached - set(tested))
     assert len(reached) == 20
+
+
+def _launcher_rule(src: str, fn: str, kernel: str, limit: str):
+    """The J -> instance rule of launcher ``fn`` as its source writes it: the ``J <= n`` chain, the instance each branch launches
+    (``kernel``: a regex whose group is the instance) and the largest J it accepts (``limit``: the regex of its refusal)."""
+    body = src[src.index(f"\nint {fn}(") if f"\nint {fn}(" in src else src.index(f"\nstatic int {fn}("):]
+    body = body[:body.index("\n}\n")]
+    cuts = [int(n) for n in re.findall(r"if \(J <= (\d+)\)", body)]
+    insts = [int(n) for n in re.findall(kernel, body)]
+    top = int(re.search(limit, body).group(1))
+    assert len(insts) == len(cuts) + 1 and cuts == sorted(cuts) and top > cuts[-1], (fn, cuts, insts, top)
+    return lambda J: None if not 1 <= J <= top else next((i for c, i in zip(cuts, insts) if J <= c), insts[-1])
+
+
+def test_head_fold_rule_covers_every_instance():
+    """tests/util.fold_instance / act_bwd_proj_instance / act_bwd_proj_wgrad_instance restate the classifier-width dispatch of
+    spgnn_linear_mean_fold_fwd / _bwd (spgnn_gemm.hip), spgnn_act_bwd_proj and spgnn_act_bwd_proj_wgrad (spgnn_kernels.hip): they
+    agree with the launchers' sources, and the widths test_hip_head_fold.py runs select every instance of each, with J on both
+    sides of every edge.  A change to a dispatch rule fails here rather than leaving an instance untested."""
+    import os
+    from tests.util import (ACT_BWD_PROJ_J, ACT_BWD_PROJ_WGRAD_J, FOLD_J, act_bwd_proj_instance, act_bwd_proj_wgrad_instance,
+                            fold_instance)
+    csrc = os.path.join(os.path.dirname(G.__file__), "csrc")
+    gemm = open(os.path.join(csrc, "spgnn_gemm.hip")).read()
+    kern = open(os.path.join(csrc, "spgnn_kernels.hip")).read()
+    kfoldj = re.search(r"constexpr int kFoldJ = (\d+);", gemm).group(1)   # the fold launchers refuse J > gemm::kFoldJ
+    gemm = gemm.replace("gemm::kFoldJ", kfoldj)
+    cases = [
+        (gemm, "spgnn_linear_mean_fold_fwd", r"linear_mean_fold_fwd_kernel<(\d+)>", r"J > (\d+)",
+         fold_instance, FOLD_J),
+        (gemm, "spgnn_linear_mean_fold_bwd", r"linear_mean_fold_bwd_kernel<(\d+)>", r"J > (\d+)",
+         fold_instance, FOLD_J),
+        (kern, "act_bwd_proj_launch", r"X\((\d+)\)", r"J > (\d+)", act_bwd_proj_instance, ACT_BWD_PROJ_J),
+        (kern, "spgnn_act_bwd_proj_wgrad", r"X\((\d+)\)", r"J > (\d+)", act_bwd_proj_wgrad_instance, ACT_BWD_PROJ_WGRAD_J),
+    ]
+    for src, fn, kernel, limit, rule, tested in cases:
+        lib_rule = _launcher_rule(src, fn, kernel, limit)
+        assert [lib_rule(J) for J in range(0, 41)] == [rule(J) for J in range(0, 41)], fn
+        every = {rule(J) for J in range(1, 41)} - {None}
+        assert {rule(J) for J in tested} == every, (fn, sorted(every))
+        for jp in every:                                                   # both sides of every edge between instances
+            if rule(jp + 1) is not None:
+                assert jp in tested and jp + 1 in tested, (fn, jp)
+        assert 1 in tested and max(J for J in range(1, 41) if rule(J) is not None) in tested, fn

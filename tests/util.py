@@ -316,3 +316,27 @@ def run_gat_raw_fp32(csc, y, s, bias, g_out, H, D, act, p, od, score):
     g_e = ops.gat_bwd_raw(csc, ft, s[:, :H], s[:, H:], attn, g_out, out if act != ops.ACT_NONE else None, H, D, 0.2, act, p, 1234,
                           g_y[:, HD:], g_y[:, :HD], g_s[:, :H], g_s[:, H:], absmax=blk2, score_l=al, score_r=ar, out_drop=out_drop)
     return dict(out=out.clone(), attn=attn, g_y=g_y, g_s=g_s, g_e=g_e, blk=blk.clone(), blk2=blk2.clone())
+
+
+# Python restatement of the J -> template instance rules of the output-head kernels (the launchers in spgnn_gemm.hip and
+# spgnn_kernels.hip): the classifier width J rounded up to the next instance, None where the launcher refuses J.
+# test_graph.test_head_fold_rule_covers_every_instance keeps them equal to the sources and checks that the shapes of
+# test_hip_head_fold.py select every instance.
+def fold_instance(J: int):
+    """spgnn_linear_mean_fold_fwd / _bwd: JP = 8 / 16 / 24 / 32."""
+    return None if not 1 <= J <= 32 else next(jp for jp in (8, 16, 24, 32) if J <= jp)
+
+
+def act_bwd_proj_instance(J: int):
+    """spgnn_act_bwd_proj: JP = 8 / 16 / 24 / 32."""
+    return None if not 1 <= J <= 32 else next(jp for jp in (8, 16, 24, 32) if J <= jp)
+
+
+def act_bwd_proj_wgrad_instance(J: int):
+    """spgnn_act_bwd_proj_wgrad: JP = 8 / 16 / 24."""
+    return None if not 1 <= J <= 24 else next(jp for jp in (8, 16, 24) if J <= jp)
+
+
+FOLD_J = (1, 8, 9, 16, 17, 22, 24, 25, 32)          # every instance and both sides of each of its edges
+ACT_BWD_PROJ_J = (1, 8, 9, 16, 17, 24, 25, 32)
+ACT_BWD_PROJ_WGRAD_J = (1, 8, 9, 16, 17, 24)
